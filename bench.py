@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — probe throughput of the MI355X hash-join hot path (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c5|pipeline] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                  [--workload c2|c3|c5|pipeline] [--no-cpu]
+  A plain run (c2, c5) sets up, warms up, times the K steps and prints the headline: metric, value,
+  unit, ms_per_step, config, phases, status flags.  --full adds everything else the line reports:
+  parity against the oracle, roofline accounting, the copy ceiling, the CPU baseline, the other
+  paths, C3 / C5 and the scaling reference.  --dump-outputs DIR writes the last timed step's outputs
+  as DIR/*.npy (dump_outputs), the same from run to run for the same arguments.
   N > 1: `python bench.py --gpus N` starts its own N rank processes (torch.distributed.run as a child
   process, before any GPU call in this one) and forwards rank 0's JSON line; launched by an outside
   torchrun (WORLD_SIZE set) it runs as that rank directly.
@@ -21,9 +27,9 @@ Step = one pass of the hot path over one batch:
   N > 1 (C4 shape, weak scaling): every rank owns the build keys with owner = h(k) >> (64-log2 N)
       and 2^30 probe keys of its own; a step = owner partition + RCCL all-to-all (xGMI) + local
       probe.
-Prints ONE JSON line on rank 0 with roofline and cpu_baseline objects.
-The default c2 line also carries `other_workloads`: C3 and C5 timed in the same run, each with its
-own parity checks and roofline (--no-other-workloads skips them).
+Prints ONE JSON line on rank 0; with --full it carries roofline and cpu_baseline objects (DESIGN.md
+§Measurement), and the c2 line also `other_workloads`: C3 and C5 timed in the same run, each with
+its own parity checks and roofline (--no-other-workloads skips them).
 """
 from __future__ import annotations
 
@@ -100,6 +106,13 @@ def parse():
     ap.add_argument("--path", default="partitioned", choices=["partitioned", "chunk", "ordered"],
                     help="partitioned: slot-range partition + L2-resident probe (L1/L2 parity); "
                          "chunk: reference-order chunk probe (L3 parity)")
+    ap.add_argument("--full", action="store_true",
+                    help="c2 / c5: beside the headline, everything else the line reports — parity against the oracle, "
+                         "roofline accounting, copy ceiling, CPU baseline, the other paths and workloads, the "
+                         "scaling reference (each of the --no-* switches below then drops its part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c2 / c5: after the timed steps, write what the last step returned as DIR/<name>.npy "
+                         "(float64; per-row match records of a fixed seeded sample of probe rows, dump_outputs)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--cpu-sample", type=int, default=1 << 28, help="probe keys in the multi-thread CPU sample")
@@ -117,6 +130,8 @@ def parse():
                     help="product | tuning (libccj_tuning.so: make tuning; A/B sweeps with its env overrides) | "
                          "a path to another build of the library (same-box A/B of two source versions)")
     a = ap.parse_args()
+    if a.dump_outputs and (a.workload not in ("c2", "c5") or a.gpus > 1 or a.sharded):
+        ap.error("--dump-outputs: single-GPU c2 / c5 only")
     if a.lib == "tuning":
         ccj.LIB_PATH = os.path.join(PKG, "libccj_tuning.so")
     elif a.lib != "product":
@@ -312,6 +327,56 @@ def phase_report(pev, path, c5=False):
             "gather_tuples_ms": mean[2],
             "kernels": {"hash_find_bucket": k[0], "match_tuples_and_advance_pointers": k[1],
                         "gather_tuples": gather_k}}
+
+
+DUMP_ROWS = 1 << 19  # probe rows in --dump-outputs' sample: at most 11 float64 arrays (C5) of 4 MB each
+
+
+def dump_outputs(dirname, res, n_probe, chunk, row_map=None):
+    """--dump-outputs: what the timed path's last step returned (count, sel, payload and, for C5, the
+    gathered payload columns of a probe output), in a form two builds can compare array for array.
+    The partitioned layout's order inside a segment differs from run to run, so the match records
+    are keyed by probe row: for a fixed seeded sample of probe rows (rows.npy), the number of
+    matches (match_count.npy), the sum of the matched payloads (payload_sum.npy) and of each payload
+    column (payload_col<c>_sum.npy).  totals.npy = [matches in the whole output, status flags, match
+    records whose row lies outside the probe column].  chunk / row_map as in ccj.result_checksum
+    (chunk 0: sel holds the row itself).  All float64 (exact below 2^53); returns the file names."""
+    os.makedirs(dirname, exist_ok=True)
+    dev = res["count"].device
+    rows = np.unique(np.random.default_rng(SEED).integers(0, n_probe, size=min(n_probe, DUMP_ROWS)))
+    slot = torch.full((n_probe,), -1, dtype=torch.int32, device=dev)  # probe row -> its place in the sample
+    slot[torch.from_numpy(rows).to(dev)] = torch.arange(len(rows), dtype=torch.int32, device=dev)
+    n_chunks, cap = res["n_chunks"], res["cap"]
+    cols = [res["payload"]] + list(res["payload_cols"])
+    acc = torch.zeros((1 + len(cols), len(rows)), dtype=torch.float64, device=dev)
+    lane = torch.arange(cap, device=dev)
+    total = stray = 0
+    per = max(1, (1 << 24) // cap)  # chunks per slice: bounded temporaries at 2^30 rows
+    for c0 in range(0, n_chunks, per):
+        cnt = res["count"][c0:min(n_chunks, c0 + per)].to(torch.int64).clamp_(0, cap)
+        idx = torch.nonzero((lane[None, :] < cnt[:, None]).reshape(-1)).squeeze(1) + c0 * cap
+        row = (res["sel"][idx].to(torch.int64) & 0xFFFFFFFF) + (idx // cap) * chunk
+        if row_map is not None:  # partitioned layout without CCJ_PART_ROWS: position -> row
+            ok = row < row_map.numel()
+            row = torch.where(ok, row_map[row.clamp_(max=row_map.numel() - 1)].to(torch.int64) & 0xFFFFFFFF,
+                              torch.full_like(row, n_probe))
+        ok = row < n_probe
+        s = slot[row.clamp_(max=n_probe - 1)].to(torch.int64)
+        keep = ok & (s >= 0)
+        s, idx = s[keep], idx[keep]
+        acc[0].index_add_(0, s, torch.ones(s.numel(), dtype=torch.float64, device=dev))
+        for j, col in enumerate(cols):
+            acc[1 + j].index_add_(0, s, col[idx].to(torch.float64))
+        total += int(cnt.sum().item())
+        stray += int((~ok).sum().item())
+    host = acc.cpu().numpy()
+    files = {"rows": rows.astype(np.float64), "match_count": host[0], "payload_sum": host[1],
+             "totals": np.array([total, int(res["status"].item()), stray], dtype=np.float64)}
+    for c in range(len(cols) - 1):
+        files[f"payload_col{c}_sum"] = host[2 + c]
+    for name, arr in files.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(arr))
+    return sorted(f + ".npy" for f in files)
 
 
 def bench_c3(args, dev, stream):
@@ -681,12 +746,13 @@ def main():
     if world > 1 or args.sharded:
         return bench_multi(args, world, rank, local, dev, stream, dist)
     line = bench_c3(args, dev, stream) if args.workload == "c3" else bench_single(args, dev, stream)
-    if args.workload == "c2" and not (args.no_other_workloads and args.no_scaling_reference):
+    beside = args.workload == "c2" and args.full  # C3, C5 and the scaling reference ride on the --full C2 line
+    if beside and not (args.no_other_workloads and args.no_scaling_reference):
         # the headline stands on its own if a later workload takes the process down
         log("[c2 line] " + json.dumps(line))
-    if args.workload == "c2" and not args.no_other_workloads:
+    if beside and not args.no_other_workloads:
         line["other_workloads"] = other_workloads(args, dev, stream)
-    if args.workload == "c2" and not args.no_scaling_reference:
+    if beside and not args.no_scaling_reference:
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
         line["scaling_reference"] = same_shape_n1(args, verify=not args.no_verify)
@@ -752,6 +818,7 @@ def other_workloads(args, dev, stream):
         # C3 keeps its CPU baseline (the reference's chaining loop on 2^26 keys of the same stream,
         # bench_c3); C5 has no reference counterpart (the reference gathers no payload columns)
         a.workload, a.path, a.no_cpu, a.no_other = w, "partitioned", args.no_cpu or w != "c3", True
+        a.dump_outputs = None  # the headline's outputs only
         a.cpu_sample = min(args.cpu_sample, 1 << 28)
         a.steps, a.warmup = max(1, min(args.steps, 10)), min(args.warmup, 2)
         t0 = time.perf_counter()
@@ -786,7 +853,7 @@ def bench_single(args, dev, stream):
     c5 = args.workload == "c5"
     P = 8 if c5 else 0
     # the rank walk is in libccj_tuning.so only: timed beside the headline with --lib tuning
-    rank_ab = args.path == "partitioned" and not c5 and not args.no_other and args.lib == "tuning"
+    rank_ab = args.full and args.path == "partitioned" and not c5 and not args.no_other and args.lib == "tuning"
     with torch.cuda.stream(stream):
         table = ccj.Table.reference(ccj.LP, n_build, 1, layout, stream=stream)
         if c5:  # C5 payload of build tuple t (key k): p_c = k*(c+1)+c, row-major [n_build, 8]
@@ -797,7 +864,8 @@ def bench_single(args, dev, stream):
             del bk, pay
         keys = ccj.gen_uniform_keys(n_probe, SEED, n_build, first_row=rank * n_probe, stream=stream)
         out = part = out_p = out_o = ws_o = None
-        every = not c5 and not args.no_other  # C2: every path (the headline and the ones timed beside it)
+        # C2 --full: every path (the headline and the ones timed beside it)
+        every = args.full and not c5 and not args.no_other
         if args.path == "chunk" or every:
             out = table.alloc_outputs(n_probe, chunk, rounds=True, payload_cols=P, pos=c5)
         if args.path == "ordered" or every:
@@ -853,12 +921,34 @@ def bench_single(args, dev, stream):
     total_tuples = n_probe * world
     value = total_tuples / (wall / args.steps)
 
-    # ---- verification + work accounting (untimed) ----
+    # ---- the last timed step's status and outputs (untimed) ----
+    res0 = out_p if args.path == "partitioned" else out_o if args.path == "ordered" else out
+    status = int(res0["status"].item())
     if args.path == "partitioned":
-        status = int(out_p["status"].item())
         if status & ccj.FLAG_PART_OVERFLOW:
             raise SystemExit("bench: fixed-capacity partition overflowed on uniform keys")
         out_p["n_chunks"] = (part["positions"] + chunk - 1) // chunk
+    line = {
+        "metric": METRIC, "value": value, "unit": "probe tuples/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64",
+        "data": "synthetic (reference key generator build side; SplitMix64 uniform probe keys, seed 42)",
+        "config": {"workload": ("C5: 1xMI355X wide-payload LP join, 64M build / 1B probe int64, 8 int64 payload "
+                                "columns gathered on match, chunk=2048") if c5 else
+                   "C2: 1xMI355X linear-probe, 64M build / 1B probe int64 uniform keys, chunk=2048",
+                   "table": "linear_probing", "layout": args.layout, "n_build": n_build,
+                   "n_probe_per_gpu": n_probe, "chunk": chunk, "parallelism": f"dp{world}"},
+        "path": args.path, "kernel_ms": kern_ms, "phases": phases, "status_flags": status,
+    }
+    if args.dump_outputs:
+        parted = args.path == "partitioned"
+        line["outputs"] = dump_outputs(args.dump_outputs, res0, n_probe, 0 if parted and rows_mode else chunk,
+                                       part["row_map"] if parted and not rows_mode else None)
+    if not args.full:  # the plain run: the headline alone
+        return line
+
+    # ---- verification + work accounting (untimed) ----
+    if args.path == "partitioned":
         if rows_mode:  # sel = the original row
             matches, l2 = ccj.result_checksum(out_p, 0, row_base=rank * n_probe, stream=stream)
         else:
@@ -866,8 +956,6 @@ def bench_single(args, dev, stream):
             matches, l2 = ccj.result_checksum(out_p, chunk, row_map=rm, stream=stream)
             del rm
     else:
-        res0 = out_o if args.path == "ordered" else out
-        status = int(res0["status"].item())
         matches, l2 = ccj.result_checksum(res0, chunk, row_base=rank * n_probe, stream=stream)
     # the other paths, timed the same way (reported beside the headline)
     others = [] if c5 or args.no_other else [q for q in ("ordered", "chunk", "partitioned") if q != args.path]
@@ -961,16 +1049,7 @@ def bench_single(args, dev, stream):
         ceiling = copy_ceiling(dev, stream)
 
     if rank == 0:
-        line = {
-            "metric": METRIC, "value": value, "unit": "probe tuples/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64",
-            "data": "synthetic (reference key generator build side; SplitMix64 uniform probe keys, seed 42)",
-            "config": {"workload": ("C5: 1xMI355X wide-payload LP join, 64M build / 1B probe int64, 8 int64 payload "
-                                    "columns gathered on match, chunk=2048") if c5 else
-                       "C2: 1xMI355X linear-probe, 64M build / 1B probe int64 uniform keys, chunk=2048",
-                       "table": "linear_probing", "layout": args.layout, "n_build": n_build,
-                       "n_probe_per_gpu": n_probe, "chunk": chunk, "parallelism": f"dp{world}"},
+        line.update({  # beside the plain run's fields
             "hbm_gbs_algorithmic": achieved,
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
@@ -999,17 +1078,15 @@ def bench_single(args, dev, stream):
                          # the same achieved rate against the copy rate measured on this box
                          "frac_of_copy_ceiling": achieved / ceiling["GBps"] if ceiling else None,
                          "frac_walked_of_copy_ceiling": achieved_walked / ceiling["GBps"] if ceiling else None},
-            "phases": phases,
             "hbm_copy_ceiling": ceiling,
             "cpu_baseline": cpu,
             "parity": parity,
-            "path": args.path,
             "other_paths": [{
                 "path": o, "ms_per_step": o_ms, "value": n_probe / (o_ms * 1e-3),
                 "frac": alg_bytes / (o_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                 "parity": "L3 (reference order)" if o not in ("partitioned", "rank") else "L1/L2",
                 "kernel": PATH_KERNELS[o], "check": o_par} for o, (o_ms, o_par) in other_runs.items()],
-        }
+        })
     return line
 
 

@@ -1,8 +1,8 @@
 """bench.py end to end at small sizes, one process per workload: the JSON line of the driver's
 contract for every workload and path (C2 partitioned with the reference-order paths beside it, and
 the tuning build's rank-walk A/B, C2 ordered, C3 with compaction, C5 with payload columns, the main.cpp pipeline),
-with the bench's own full-size-style parity checks green.  Catches a broken bench path before the
-driver's round-end run does."""
+with the bench's own full-size-style parity checks green (bench.py --full), and the plain run with
+its --dump-outputs arrays.  Catches a broken bench path before the driver's round-end run does."""
 import json
 import os
 import subprocess
@@ -17,13 +17,48 @@ SMALL = ["--steps", "2", "--warmup", "1", "--no-cpu", "--n-build", str(1 << 21),
 
 
 def run_bench(*extra):
-    p = subprocess.run([sys.executable, "bench.py", *SMALL, *extra], cwd=ROOT, capture_output=True, text=True,
-                       timeout=300)
+    """bench.py --full at small sizes: the line with its parity checks and roofline."""
+    p = subprocess.run([sys.executable, "bench.py", "--full", *SMALL, *extra], cwd=ROOT, capture_output=True,
+                       text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
     assert line["value"] > 0 and line["n_gpus"] == 1 and line["higher_is_better"]
     assert "roofline" in line and line["roofline"]["frac"] > 0
     return line
+
+
+@pytest.mark.parametrize("extra", [(), ("--no-rows",), ("--path", "chunk"), ("--workload", "c5")],
+                         ids=["c2", "c2-no-rows", "c2-chunk", "c5"])
+def test_bench_plain_run_dumps_outputs(tmp_path, extra):
+    """A plain run: the headline alone (no parity, roofline, CPU baseline or other paths), the number
+    of timed steps as asked, and --dump-outputs' per-row match records equal to the exact answer
+    (the probe keys and the build keys from the oracle's generators)."""
+    import numpy as np
+    from oracle import oracle as O
+    n_build, n_probe = 1 << 21, 1 << 24
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--n-build",
+                        str(n_build), "--n-probe", str(n_probe), "--dump-outputs", str(tmp_path), *extra], cwd=ROOT,
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 3 and line["status_flags"] == 0
+    assert line["value"] == pytest.approx(n_probe / (line["ms_per_step"] * 1e-3))
+    assert line["unit"] == "probe tuples/s" and line["higher_is_better"] and line["dtype"] == "int64"
+    for k in ("roofline", "parity", "cpu_baseline", "other_paths", "other_workloads", "scaling_reference"):
+        assert k not in line
+    got = {f[:-4]: np.load(tmp_path / f) for f in line["outputs"]}
+    assert sorted(os.listdir(tmp_path)) == line["outputs"]
+    assert all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    rows = got["rows"].astype(np.int64)
+    assert len(rows) > 1 << 18 and np.all(np.diff(rows) > 0) and rows[-1] < n_probe
+    keys = O.uniform_keys(42, 0, n_probe, n_build)[rows]
+    hit = np.isin(keys, O.ref_build_keys(n_build, 1))
+    assert hit.any()
+    assert np.array_equal(got["match_count"], hit.astype(np.float64))
+    assert np.array_equal(got["payload_sum"], np.where(hit, keys, 0).astype(np.float64))
+    assert got["totals"][1] == 0 and got["totals"][2] == 0 and got["totals"][0] >= hit.sum()
+    for c in range(8 if "c5" in extra else 0):  # C5's build payload columns: p_c = k * (c + 1) + c
+        assert np.array_equal(got[f"payload_col{c}_sum"], np.where(hit, keys * (c + 1) + c, 0).astype(np.float64))
 
 
 def test_bench_c2_with_other_paths():

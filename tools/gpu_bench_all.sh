@@ -7,12 +7,12 @@ run() {
 import json,sys;d=json.loads(sys.stdin.read());r=d.get('roofline') or {}
 print('$*', '|', round(d['ms_per_step'],3), 'ms |', round(d['value']/1e9,2), 'G/s | frac', r.get('frac') and round(r['frac'],4), '|', {k:v for k,v in d['parity'].items() if k in ('l1_ok','l2_ok','payload_cols_ok','equals_chunk_path_l3','compaction_keeps_all','modes_agree')})" >> gpurun_out/bench_all.log
 }
-run --no-cpu --no-other
-run --no-cpu --no-other --path ordered
-run --no-cpu --no-other --path chunk
+run --full --no-cpu --no-other
+run --full --no-cpu --no-other --path ordered
+run --full --no-cpu --no-other --path chunk
 run --no-cpu --workload c3
 run --no-cpu --workload c3 --path ordered
-run --no-cpu --workload c5
+run --full --no-cpu --workload c5
 run --no-cpu --workload pipeline
 run --gpus 1 --sharded --no-cpu --steps 5 --warmup 2
 cat gpurun_out/bench_all.log
