@@ -39,7 +39,7 @@ class CCJError(RuntimeError):
 
 class TableInfo(C.Structure):
     _fields_ = [("kind", C.c_int32), ("layout", C.c_int32), ("n_keys", C.c_uint64), ("size", C.c_uint64),
-                ("max_dup", C.c_uint64), ("max_rounds", C.c_uint32), ("reserved", C.c_uint32),
+                ("max_dup", C.c_uint64), ("max_rounds", C.c_uint32), ("slot32", C.c_uint32),
                 ("d_table", C.c_void_p), ("d_bucket_off", C.c_void_p)]
 
 
@@ -82,7 +82,7 @@ EXPORTS = ["ccj_last_error", "ccj_abi_version", "ccj_device_init", "ccj_table_bu
            "ccj_probe_ordered_workspace_size", "ccj_probe_ordered", "ccj_probe_visits",
            "ccj_stream_create_cu_masked", "ccj_stream_destroy", "ccj_device_cus", "ccj_copy_device",
            "ccj_table_get_arrays", "ccj_probe_cost_walk", "ccj_set_phase_events", "ccj_build_hash",
-           "ccj_last_gather_kernel"]
+           "ccj_last_gather_kernel", "ccj_table_drop_slot32"]
 
 MAX_JOINS = 8
 COMPACT_NONE, COMPACT_FULL = 0, 1
@@ -122,6 +122,8 @@ def lib():
         L.ccj_table_get_info.argtypes = [vp, C.POINTER(TableInfo)]
         L.ccj_table_get_arrays.argtypes = [vp, C.POINTER(TableArrays)]
         L.ccj_table_free.argtypes = [vp]
+        if hasattr(L, "ccj_table_drop_slot32"):  # (absent in an older ABI-15 build: bench.py --lib A/B)
+            L.ccj_table_drop_slot32.argtypes = [vp]
         L.ccj_table_set_payload.argtypes = [vp, vp, C.c_uint32, vp]
         L.ccj_table_build_rank_index.argtypes = [vp, vp]
         L.ccj_probe_partitioned_workspace_size.restype = C.c_size_t
@@ -319,6 +321,7 @@ class Table:
         self.n_keys, self.size = info.n_keys, info.size
         self.max_dup, self.max_rounds = info.max_dup, info.max_rounds
         self.d_table, self.d_bucket_off = info.d_table, info.d_bucket_off
+        self.slot32 = bool(info.slot32)  # LP: the 32-bit slot array exists (ccj.h ccj_table_drop_slot32)
 
     @classmethod
     def reference(cls, kind: int, n: int, cf: int = 1, layout: int = LAYOUT_REFERENCE, stream=None):
@@ -342,6 +345,12 @@ class Table:
         check(lib().ccj_table_build_on_device(kind, _ptr(d_keys), d_keys.numel(), _stream(stream), C.byref(h)),
               "ccj_table_build_on_device")
         return cls(h)
+
+    def drop_slot32(self):
+        """Free the table's 32-bit slot array (size * 4 bytes; ccj_table_drop_slot32): later partitioned
+        probes walk the 8-byte slots.  Idempotent."""
+        check(lib().ccj_table_drop_slot32(self._h), "ccj_table_drop_slot32")
+        self.slot32 = False
 
     def free(self):
         if self._h:

@@ -196,6 +196,33 @@ int build_rank_index(ccj_table *, hipStream_t) {
 }
 #endif
 
+// The 32-bit slot array (ccj_table::d_slot32) from the finished slot array, at the end of every LP
+// build: kept for tables of distinct keys (only the first-match walk reads it) that all lie in
+// [0, 0xFFFFFFFE] and of >= 32 slots (one 8-slot window inside a 32-slot line).  Build-time work on
+// the build's stream.  Without the memory for it (size * 4 bytes) the table simply has none.
+int build_slot32(ccj_table *t, hipStream_t s) {
+  t->info.slot32 = 0;
+  if (t->info.kind != CCJ_TABLE_LP || t->info.max_dup > 1 || t->info.size < 32 || t->d_slot32) return CCJ_OK;
+  const uint64_t size = t->info.size;
+  uint32_t *d32 = nullptr, *d_bad = nullptr, h_bad = 1;
+  if (hipMalloc((void **)&d32, size * sizeof(uint32_t)) != hipSuccess) {
+    (void)hipGetLastError();
+    return CCJ_OK;
+  }
+  hipError_t e = hipMalloc((void **)&d_bad, sizeof(uint32_t));
+  if (e == hipSuccess) e = ccj::launch_lp_slot32(t->d_table, size, d32, d_bad, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(&h_bad, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (d_bad) (void)hipFree(d_bad);
+  if (e != hipSuccess || h_bad) {
+    (void)hipFree(d32);
+    return e != hipSuccess ? hip_fail(e, "LP 32-bit slot array") : CCJ_OK;
+  }
+  t->d_slot32 = d32;
+  t->info.slot32 = 1;
+  return CCJ_OK;
+}
+
 int build_lp_host(const int64_t *keys, uint64_t n, ccj_table **out) {
   const uint64_t size = lp_num_slots(n);
   if (size > (1ull << 32)) return fail(CCJ_ERR_LIMIT, "LP table larger than 2^32 slots");
@@ -229,6 +256,12 @@ int build_lp_host(const int64_t *keys, uint64_t n, ccj_table **out) {
   t->d_row = (uint32_t *)d;
   t->info.d_table = t->d_table;
   (void)hipGetDevice(&t->device);
+  rc = build_slot32(t.get(), nullptr);
+  if (rc) {
+    (void)hipFree(t->d_table);
+    (void)hipFree(t->d_row);
+    return rc;
+  }
   *out = t.release();
   return CCJ_OK;
 }
@@ -413,6 +446,10 @@ int build_lp_device(const int64_t *d_keys, uint64_t n, hipStream_t s, uint64_t k
   t->info.max_dup = dup ? dup : 1;
   t->info.d_table = t->d_table;
   (void)hipGetDevice(&t->device);
+  if (int rc = build_slot32(t.get(), s)) {
+    cleanup();
+    return rc;
+  }
   *out = t.release();
   return CCJ_OK;
 }
@@ -558,8 +595,17 @@ int ccj_table_build_rank_index(ccj_table *t, ccj_stream stream) {
   return build_rank_index(t, (hipStream_t)stream);
 }
 
+int ccj_table_drop_slot32(ccj_table *t) {
+  if (!t) return CCJ_OK;
+  if (t->d_slot32) (void)hipFree(t->d_slot32);
+  t->d_slot32 = nullptr;
+  t->info.slot32 = 0;
+  return CCJ_OK;
+}
+
 int ccj_table_free(ccj_table *t) {
   if (!t) return CCJ_OK;
+  if (t->d_slot32) (void)hipFree(t->d_slot32);
   if (t->d_table) (void)hipFree(t->d_table);
   if (t->d_off) (void)hipFree(t->d_off);
   if (t->d_bucket) (void)hipFree(t->d_bucket);
@@ -699,6 +745,7 @@ int ccj_probe_partitioned(const ccj_table *t, const ccj_probe_args *a, uint32_t 
   PhaseScope phase_scope((hipStream_t)stream);
   ccj::ProbeParams p;
   if (int rc = fill_probe_params(t, a, p)) return rc;
+  p.table32 = t->d_slot32;  // (probe_walk2 alone reads it: 2 MiB windows instead of 4)
   if (t->info.kind == CCJ_TABLE_CHAIN && (a->out_pos || a->n_payload_cols))
     return fail(CCJ_ERR_INVALID, "ccj_probe_partitioned: positions / payload columns need an LP table");
   if (a->sel) return fail(CCJ_ERR_INVALID, "ccj_probe_partitioned: sel must be NULL");

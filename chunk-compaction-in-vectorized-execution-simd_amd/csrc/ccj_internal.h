@@ -32,6 +32,11 @@ struct ccj_table {
   uint32_t *d_pre = nullptr;
   int64_t *d_ckeys = nullptr;
   uint32_t rank_wbits = 0;
+  // LP, optional (info.slot32): the slot array with 4-byte slots — the low word of each slot's key,
+  // 0xFFFFFFFF = empty, `size` slots — for tables of distinct keys in [0, 0xFFFFFFFE] with >= 32
+  // slots; the partitioned first-match walk (probe_walk2) reads it instead of d_table, so a
+  // partition's window takes half the L2.  Built with the table, constant across probe calls.
+  uint32_t *d_slot32 = nullptr;
 };
 
 namespace ccj {
@@ -77,6 +82,9 @@ constexpr uint32_t kMaxParts = 64;  // owner partitions (GPUs) per multisplit
 
 struct ProbeParams {
   const int64_t *table;
+  // LP, optional (ccj_probe_partitioned): the table's 32-bit slot array (ccj_table::d_slot32), read
+  // by probe_walk2 in place of `table`; every other kernel reads `table`
+  const uint32_t *table32;
   const uint32_t *off;
   // chain only, optional: bucket records {start | len << 32, first key} — one 16-byte load gives
   // the chain's range and its round-0 candidate (most chains at load 1/2 have one key)
@@ -205,6 +213,9 @@ hipError_t launch_scatter_payload(const int64_t *src, uint32_t n_cols, const uin
 // Largest multiplicity of one key (max_run = longest occupied run bounds the walk).
 hipError_t launch_lp_max_dup(const int64_t *slots, uint64_t n_slots, uint32_t max_run, uint32_t *out, hipStream_t s);
 hipError_t launch_lp_runs(const int64_t *slots, uint64_t n_slots, uint32_t *seg_stats, hipStream_t s);
+// The 32-bit slot array (ccj_table::d_slot32) of a finished LP slot array; *bad (device) = 1 when
+// an occupied slot's key lies outside [0, 0xFFFFFFFE].
+hipError_t launch_lp_slot32(const int64_t *slots, uint64_t n_slots, uint32_t *slot32, uint32_t *bad, hipStream_t s);
 // The chaining table built on the device (ccj_build.hip): stable bucket sort -> CSR, row map,
 // 16- and 8-byte bucket records, longest chain; known_dup = 0: max_dup computed from the keys.
 int build_chain_device(const int64_t *d_keys, uint64_t n, hipStream_t s, uint64_t known_dup, ccj_table **out);

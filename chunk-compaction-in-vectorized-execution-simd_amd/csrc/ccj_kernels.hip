@@ -2810,9 +2810,16 @@ __device__ __forceinline__ void stage_keys_aux(const int64_t *keys, uint32_t phy
 // (Round 5: an MM form for the ordered route — every row walking its whole run, phase A's
 // continuing rows keeping their first window's hits — measured slower than probe_walk1<MM>: 7.75
 // against 7.49 ms, same box; the ~16 % of rows that go on are walked lane by lane in phase B.)
-template <bool POS, int NB = 1>
+// S32: the windows come from the table's 32-bit slot array (p.table32, ccj_table::d_slot32: the low
+// word of every slot's key, 0xFFFFFFFF = empty; only tables whose keys all lie in [0, 0xFFFFFFFE]
+// have one).  Same two 16-byte DMA halves per row into the same ring, so a window is 8 slots and a
+// partition's window takes half the bytes of L2.  A probe key with a high word cannot be in such a
+// table: its row is a miss without a look (it still issues, slot 0's window, like an idle lane).
+template <bool POS, int NB = 1, bool S32 = false>
 __global__ __launch_bounds__(kWave * 4, POS && NB == 1 ? 5 : 1) void probe_walk2(ProbeParams p) {
   constexpr int NW = 4;
+  constexpr uint32_t kW = S32 ? 8u : (uint32_t)kWin;  // slots per 32-byte window
+  constexpr uint32_t kLine = S32 ? 32u : 16u;          // slots per 128-byte line
   constexpr uint32_t kWaveRows = kMaxChunk / NW;      // rows per wave
   constexpr int kJ = (int)(kWaveRows / kWave);         // row groups (phase-A steps) per wave
   __shared__ Walk1Shared<NB, NW> sm;
@@ -2871,14 +2878,16 @@ __global__ __launch_bounds__(kWave * 4, POS && NB == 1 ? 5 : 1) void probe_walk2
   const uint32_t ring_lds = (uint32_t)__builtin_amdgcn_readfirstlane(
       (int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)ring);
   const char *win = ring + (lane & 1u) * 1024 + (lane >> 1) * 32;  // this lane's window, once landed
-  const uint32_t last_start = p.mask - (kWin - 1);  // table size - window (size >= 16)
-  const uint32_t half = (lane & 1u) * 2u;
-  // the window [s, s + kWin) that holds slot `cur` (never past the table's end or its 128-byte line)
+  const uint32_t last_start = p.mask - (kW - 1u);  // table size - window (size >= 16; S32: >= 32)
+  const uint32_t half = (lane & 1u) * (kW / 2u);
+  // the window [s, s + kW) that holds slot `cur` (never past the table's end or its 128-byte line)
   auto start = [&](uint32_t cur) {
     uint32_t s = cur < last_start ? cur : last_start;
-    const uint32_t lim = (s & ~15u) + (16u - kWin);
+    const uint32_t lim = (s & ~(kLine - 1u)) + (kLine - kW);
     return s < lim ? s : lim;
   };
+  // S32: a key with a high word (negative keys too) is in no table that has a 32-bit slot array
+  auto in_range = [&](int64_t kk) { return !S32 || ((uint64_t)kk >> 32) == 0u; };
   // Every lane issues (an idle one loads slot 0's line), and with all lanes active: the DPP moves
   // read the pair's other lane, so a lane switched off here would hand its partner a stale address.
   // The callers keep these in uniform control flow (phase B's loop exits on a ballot, like
@@ -2890,19 +2899,35 @@ __global__ __launch_bounds__(kWave * 4, POS && NB == 1 ? 5 : 1) void probe_walk2
     dpp_check(p, a, a0, a1, lane);  // (tuning build: the DPP gave the partner lanes' own addresses)
     a0 = a0 < last_start ? a0 : last_start;  // (a guard: whatever a DPP returns, the DMA stays in the table)
     a1 = a1 < last_start ? a1 : last_start;
-    dma16(p.table + a0 + half, ring_lds + slot * kRingSlot);
-    dma16(p.table + a1 + half, ring_lds + slot * kRingSlot + 1024u);
+    if (S32) {
+      dma16(p.table32 + a0 + half, ring_lds + slot * kRingSlot);
+      dma16(p.table32 + a1 + half, ring_lds + slot * kRingSlot + 1024u);
+    } else {
+      dma16(p.table + a0 + half, ring_lds + slot * kRingSlot);
+      dma16(p.table + a1 + half, ring_lds + slot * kRingSlot + 1024u);
+    }
   };
   // the landed window against key kk from slot cur (window start s): hits (bits from cur) and
   // whether the run ends inside the window
   auto look = [&](int64_t kk, uint32_t cur, uint32_t s, uint32_t &hits, uint32_t slot) {
-    const longlong2 x0 = *reinterpret_cast<const longlong2 *>(win + slot * kRingSlot);
-    const longlong2 x1 = *reinterpret_cast<const longlong2 *>(win + slot * kRingSlot + 16);
-    const uint32_t e = (x0.x == -1 ? 1u : 0u) | (x0.y == -1 ? 2u : 0u) | (x1.x == -1 ? 4u : 0u) | (x1.y == -1 ? 8u : 0u);
-    const uint32_t m = (x0.x == kk ? 1u : 0u) | (x0.y == kk ? 2u : 0u) | (x1.x == kk ? 4u : 0u) | (x1.y == kk ? 8u : 0u);
+    uint32_t e, m;
+    if (S32) {
+      const uint4 y0 = *reinterpret_cast<const uint4 *>(win + slot * kRingSlot);
+      const uint4 y1 = *reinterpret_cast<const uint4 *>(win + slot * kRingSlot + 16);
+      const uint32_t k32 = (uint32_t)kk, none = 0xFFFFFFFFu;
+      e = (y0.x == none ? 1u : 0u) | (y0.y == none ? 2u : 0u) | (y0.z == none ? 4u : 0u) | (y0.w == none ? 8u : 0u) |
+          (y1.x == none ? 16u : 0u) | (y1.y == none ? 32u : 0u) | (y1.z == none ? 64u : 0u) | (y1.w == none ? 128u : 0u);
+      m = (y0.x == k32 ? 1u : 0u) | (y0.y == k32 ? 2u : 0u) | (y0.z == k32 ? 4u : 0u) | (y0.w == k32 ? 8u : 0u) |
+          (y1.x == k32 ? 16u : 0u) | (y1.y == k32 ? 32u : 0u) | (y1.z == k32 ? 64u : 0u) | (y1.w == k32 ? 128u : 0u);
+    } else {
+      const longlong2 x0 = *reinterpret_cast<const longlong2 *>(win + slot * kRingSlot);
+      const longlong2 x1 = *reinterpret_cast<const longlong2 *>(win + slot * kRingSlot + 16);
+      e = (x0.x == -1 ? 1u : 0u) | (x0.y == -1 ? 2u : 0u) | (x1.x == -1 ? 4u : 0u) | (x1.y == -1 ? 8u : 0u);
+      m = (x0.x == kk ? 1u : 0u) | (x0.y == kk ? 2u : 0u) | (x1.x == kk ? 4u : 0u) | (x1.y == kk ? 8u : 0u);
+    }
     const uint32_t off = cur - s;
     const uint32_t ee = e >> off;
-    const uint32_t f = (uint32_t)__builtin_ctz(ee | ((1u << kWin) >> off));  // run end (or window end) past cur
+    const uint32_t f = (uint32_t)__builtin_ctz(ee | ((1u << kW) >> off));  // run end (or window end) past cur
     hits = (m >> off) & ((1u << f) - 1u);
     return ee != 0u || hits != 0u;
   };
@@ -2915,7 +2940,7 @@ __global__ __launch_bounds__(kWave * 4, POS && NB == 1 ? 5 : 1) void probe_walk2
   uint32_t cont = 0;
   uint32_t sa[kJ];
 #pragma unroll
-  for (int j = 0; j < kJ; ++j) sa[j] = start(h[j]);
+  for (int j = 0; j < kJ; ++j) sa[j] = in_range(k[j]) ? start(h[j]) : 0u;  // (out of range: slot 0's window, unread)
   if (NB > 1) issue(w0 < wend ? sa[0] : 0u, 0u);
 #pragma unroll
   for (int j = 0; j < kJ; ++j) {
@@ -2936,10 +2961,12 @@ __global__ __launch_bounds__(kWave * 4, POS && NB == 1 ? 5 : 1) void probe_walk2
     }
     if (valid) {
       uint32_t hits;
-      if (look(k[j], h[j], s, hits, NB > 1 ? (uint32_t)j & 1u : 0u)) {
+      if (!in_range(k[j])) {
+        sm.hc[i] = result(h[j], 0u);  // a miss
+      } else if (look(k[j], h[j], s, hits, NB > 1 ? (uint32_t)j & 1u : 0u)) {
         sm.hc[i] = result(h[j], hits);
       } else {
-        sm.hc[i] = (s + kWin) & p.mask;  // the next unread slot
+        sm.hc[i] = (s + kW) & p.mask;  // the next unread slot
         cont |= 1u << j;
       }
     }
@@ -2971,7 +2998,7 @@ __global__ __launch_bounds__(kWave * 4, POS && NB == 1 ? 5 : 1) void probe_walk2
           sm.hc[bi] = result(bcur, hits);
           have = false;
         } else {
-          bcur = (bst + kWin) & p.mask;
+          bcur = (bst + kW) & p.mask;
         }
       }
       take();
@@ -3327,10 +3354,15 @@ hipError_t launch_probe_flat(int kind, const ProbeParams &p, hipStream_t s) {
   // pipeline (each slot re-issued as soon as it is consumed, vmcnt(R - 1) waits) 10.4-10.5 ms;
   // write-through (sc1) or plain output stores 10.2 ms vs non-temporal.
   const bool walk2 = p.first_match && ccj_tune_int("CCJ_WALK2", 1);
+  // probe_walk2 over the 32-bit slot array where the table has one (8-slot windows: size >= 32)
+  const bool s32 = walk2 && p.table32 && size >= 32 && ccj_tune_int("CCJ_SLOT32", 1);
   if (p.out_pos && p.rows_in_sel) {
     // C5 under CCJ_PART_ROWS (distinct keys, tables of <= 2^31 slots): the split wrote rows and keys,
     // the walk leaves each row's matched slot at its output slot
-    if (walk2 && ccj_tune_int("CCJ_WALK2_POS_NB", 1) == 2) hipLaunchKernelGGL((probe_walk2<true, 2>), g, b, 0, s, p);
+    if (walk2 && ccj_tune_int("CCJ_WALK2_POS_NB", 1) == 2) {
+      if (s32) hipLaunchKernelGGL((probe_walk2<true, 2, true>), g, b, 0, s, p);
+      else hipLaunchKernelGGL((probe_walk2<true, 2>), g, b, 0, s, p);
+    } else if (walk2 && s32) hipLaunchKernelGGL((probe_walk2<true, 1, true>), g, b, 0, s, p);
     else if (walk2) hipLaunchKernelGGL((probe_walk2<true>), g, b, 0, s, p);
     else hipLaunchKernelGGL((probe_walk1<1, false, true>), g, b, 0, s, p);
   } else if (p.out_pos) {
@@ -3354,8 +3386,11 @@ hipError_t launch_probe_flat(int kind, const ProbeParams &p, hipStream_t s) {
     // distinct keys, no rounds: fixed first windows (step j + 1's fetched while step j's are
     // checked: 40 KiB, 4 workgroups per CU), then the rows that go on.  Same box, C2 step:
     // 11.34 / 11.36 ms against 11.47 / 11.39 with one window batch in flight (5 workgroups per CU)
-    else if (walk2 && ccj_tune_int("CCJ_WALK2_NB", 2) == 1)
-      hipLaunchKernelGGL((probe_walk2<false, 1>), g, b, 0, s, p);
+    else if (walk2 && ccj_tune_int("CCJ_WALK2_NB", 2) == 1) {
+      if (s32) hipLaunchKernelGGL((probe_walk2<false, 1, true>), g, b, 0, s, p);
+      else hipLaunchKernelGGL((probe_walk2<false, 1>), g, b, 0, s, p);
+    } else if (walk2 && s32)
+      hipLaunchKernelGGL((probe_walk2<false, 2, true>), g, b, 0, s, p);
     else if (walk2)
       hipLaunchKernelGGL((probe_walk2<false, 2>), g, b, 0, s, p);
     else if (ccj_tune_int("CCJ_WALK_NW", 4) == 8)  // 8 waves x 256 rows: 40 KiB, 4 workgroups = 32 waves per CU
@@ -3971,6 +4006,31 @@ hipError_t launch_lp_max_dup(const int64_t *slots, uint64_t n_slots, uint32_t ma
   const uint64_t want = (n_slots + 255) / 256;
   hipLaunchKernelGGL(lp_max_dup, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(256), 0, s, slots, n_slots,
                      max_run, out);
+  return hipGetLastError();
+}
+
+namespace {
+// The 32-bit slot array of a finished LP slot array: the low word of every occupied slot's key,
+// 0xFFFFFFFF for an empty slot; *bad is raised when an occupied slot's key lies outside
+// [0, 0xFFFFFFFE] (the array then cannot stand for the table).  One streaming pass.
+__global__ __launch_bounds__(256) void lp_slot32(const int64_t *slots, uint64_t n_slots, uint32_t *out, uint32_t *bad) {
+  bool b = false;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_slots;
+       i += (uint64_t)gridDim.x * blockDim.x) {
+    const int64_t k = slots[i];
+    b = b || (k != -1 && (uint64_t)k > 0xFFFFFFFEull);
+    out[i] = k == -1 ? 0xFFFFFFFFu : (uint32_t)k;
+  }
+  if (__ballot(b) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(bad, 1u);
+}
+}  // namespace
+
+hipError_t launch_lp_slot32(const int64_t *slots, uint64_t n_slots, uint32_t *slot32, uint32_t *bad, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(bad, 0, sizeof(uint32_t), s);
+  if (e != hipSuccess || n_slots == 0) return e;
+  const uint64_t want = (n_slots + 255) / 256;
+  hipLaunchKernelGGL(lp_slot32, dim3((unsigned)(want < 16384 ? want : 16384)), dim3(256), 0, s, slots, n_slots,
+                     slot32, bad);
   return hipGetLastError();
 }
 

@@ -77,7 +77,8 @@ typedef struct ccj_table_info {
   uint64_t max_dup;       /* largest multiplicity of one key = max matches per probe row */
   uint32_t max_rounds;    /* largest number of Next rounds any probe chunk can take
                              (LP: longest occupied run; chain: longest chain) */
-  uint32_t reserved;
+  uint32_t slot32;        /* 1: the LP table carries its 32-bit slot array (below), 0: it does not
+                             (formerly `reserved`, always 0: same offset and type) */
   const int64_t *d_table; /* LP: slots int64[size]; chain: chain keys int64[n_keys] */
   const uint32_t *d_bucket_off; /* chain: uint32[size + 1] CSR offsets; LP: NULL */
 } ccj_table_info;
@@ -152,6 +153,20 @@ int ccj_table_get_arrays(const ccj_table *table, ccj_table_arrays *arrays);
  * extension the BASELINE config asks for. */
 int ccj_table_set_payload(ccj_table *table, const int64_t *d_payload, uint32_t n_cols, ccj_stream stream);
 int ccj_table_free(ccj_table *table);
+/* The 32-bit slot array of an LP table (ccj_table_info.slot32): a second copy of the slot array
+ * with 4-byte slots — the low word of each slot's key, 0xFFFFFFFF for an empty slot — built on the
+ * device at the end of every LP build (all three builders), from the finished table, and constant
+ * across probe calls.  A table has one when its keys are distinct (max_dup 1), every key lies in
+ * [0, 0xFFFFFFFE] and it has >= 32 slots; it costs size * 4 more bytes of device memory (1 GiB at
+ * C2's 2^28 slots; a table without the memory for it is built without).  ccj_probe_partitioned's
+ * first-match walk then reads it in place of the 8-byte slots, so a partition's window is 2 MiB
+ * instead of 4 MiB of an XCD's 4 MiB L2; results are the same, and a probe key outside the range
+ * is a miss.  Every other path reads the 8-byte slots.
+ * ccj_table_drop_slot32 frees the array and clears the flag (later probes walk the 8-byte slots):
+ * the way to give the memory back.  Idempotent; CCJ_OK for any table (chaining, none, NULL).  Not to
+ * be called while a probe of the table is in flight.  No reference counterpart (the reference has
+ * one slot array, linear_probing_ht.h:66). */
+int ccj_table_drop_slot32(ccj_table *table);
 /* The rank walk's window index (CCJ_PART_RANK): occupancy bits, occupied-slot ranks per 128 slots
  * and the occupied slots' keys in slot order, built on the device from the finished LP table
  * (size/8 + size/32 + n_keys*8 bytes: 560 MiB at C2).  A no-op for tables the rank walk does not
@@ -234,7 +249,8 @@ int ccj_probe_visits(const ccj_table *table, const int64_t *d_keys, const uint32
 
 /* Slot-range-partitioned probe (the throughput path; L1/L2 parity, not L3 order).
  * LP tables only.  The probe column (args->keys, n_rows < 2^32; sel and counts must be NULL) is
- * first split by its home slot's partition (slot >> 19: 4 MiB of table per partition, at most 1024 partitions), then
+ * first split by its home slot's partition (slot >> 19: 4 MiB of table per partition, 2 MiB where
+ * `slot32` exists (ccj_table_drop_slot32), at most 1024 partitions), then
  * probed chunk by chunk like ccj_probe with consecutive chunks kept on one XCD, so each
  * partition's table window is read from L2 instead of as random HBM lines.
  *
